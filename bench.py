@@ -9,21 +9,25 @@ time ... at 1/2/4/8 MI355X", configs[3]/[4]): FULL chain (discriminator, polypha
 recovery, sync correlator/framer, demap, de-randomise/de-interleave/de-puncture, soft Viterbi,
 Golay, LICH/LSF bookkeeping) at 16,384 channels per GPU, SIXTEEN blocks (640 ms of signal) per step
 since round 5 -- the launch size at which the library's wave-per-channel FIR stage applies (whole
-sixteen-block tiles); rounds 1-4 ran twelve, and the line still carries that
-step as `step_12_blocks`.  The FIR-stage figures ride along as nested objects -- `fir_stage`
-(configs[1]: 1,024 channels x 50 blocks), `fir_stage_16384` (the headline's batch and launch size),
-`fir_stage_16384x12` and `fir_stage_16384x48` -- so that north_star's 40 %-of-HBM target on that
-stage stays visible in the same line, each with its launch size and buffering latency in `workload`.
+sixteen-block tiles); rounds 1-4 ran twelve.
+
+A plain run does only what the headline needs: set-up, settle, W warm-up steps, K timed steps,
+--dump-outputs if given, and the line.  --full adds what takes runs of its own, as nested objects:
+the step of rounds 1-4 (`step_12_blocks`), the AWGN workload (`noisy`), two contexts on two streams
+(`two_contexts`), the FIR-stage figures -- `fir_stage` (configs[1]: 1,024 channels x 50 blocks),
+`fir_stage_16384` (the headline's batch and launch size), `fir_stage_16384x12` and
+`fir_stage_16384x48`, so that north_star's 40 %-of-HBM target on that stage stays visible, each with
+its launch size and buffering latency in `workload` -- the CPU baseline and, for N>1, the fan-out legs.
 
 `python bench.py --gpus N` starts the N ranks itself (one process per GPU, RCCL), unless it is
 already running as a rank of an external launcher (WORLD_SIZE set, e.g. torch.distributed.run).
 The parent process never touches the GPU.
 
 Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (live HIP-event
-kernel durations on the launch stream against algorithmic bytes), `cpu_baseline` (the CPU oracle
-timed on this host on a bounded sample, N=1 only), `fir_stage` (N=1 only) and, for N>1, the
-separately timed RCCL fan-out legs `fanout_ms` / `gather_ms` (compute-only `value` and
-the with-fan-out figure are both reported).
+kernel durations of the timed calls on the launch stream against algorithmic bytes) and, with
+--full, `cpu_baseline` (the CPU oracle timed on this host on a bounded sample, N=1 only),
+`fir_stage` (N=1 only) and, for N>1, the separately timed RCCL fan-out legs `fanout_ms` /
+`gather_ms` (compute-only `value` and the with-fan-out figure are both reported).
 """
 import argparse
 import json
@@ -43,6 +47,8 @@ BYTES_FRONT = 7680 + 768              # IQ in + symbols out per 
 BYTES_FULL = 7680 + 64                # IQ in + 64-byte record out
 KNAMES = ["k_frontend", "k_sync_frame", "k_worklist+k_decode", "k_bookkeeping"]
 EXIT_FANOUT_ABANDONED = 3             # the watchdog ended hung transfer legs: the line was printed WITHOUT them (a crash is 1, a signal > 128)
+DUMP_BUDGET = 63_900_000              # bytes of arrays per --dump-outputs: under 64 MB with the .npy headers
+DUMP_SEED = 0x4D313744                # channel sample of --dump-outputs when all channels would not fit
 
 
 def parse_args(argv=None):
@@ -61,15 +67,20 @@ def parse_args(argv=None):
     ap.add_argument("--gen", choices=["gpu", "host"], default="gpu",
                     help="signal source: m17gpu_gen_batch on the device (every channel distinct) or the host generator")
     ap.add_argument("--signal-gb", type=float, default=40.0, help="distinct signal kept in HBM per GPU before the stream wraps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fir-stage", action="store_true", help="skip the nested FIR-stage measurements (configs[1] and 16,384 channels)")
-    ap.add_argument("--no-step12", action="store_true", help="skip the nested full-chain step of twelve blocks (the headline of rounds 1-4)")
-    ap.add_argument("--no-noisy", action="store_true", help="skip the nested measurement on the AWGN workload of configs[3]")
-    ap.add_argument("--no-fanout", action="store_true", help="N>1: skip the separately timed RCCL scatter/gather legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the nested legs (step_12_blocks, noisy, two_contexts, fir_stage*), the CPU baseline and, for N>1, "
+                         "the fan-out legs; without it the run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's channels) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fir-stage", action="store_true", help="--full: skip the nested FIR-stage measurements (configs[1] and 16,384 channels)")
+    ap.add_argument("--no-step12", action="store_true", help="--full: skip the nested full-chain step of twelve blocks (the headline of rounds 1-4)")
+    ap.add_argument("--no-noisy", action="store_true", help="--full: skip the nested measurement on the AWGN workload of configs[3]")
+    ap.add_argument("--no-fanout", action="store_true", help="skip the separately timed RCCL scatter/gather legs")
     ap.add_argument("--fanout", choices=["torch", "capi"], default=None,
-                    help="transport of the fan-out legs: m17_sdr_amd/shard.py over torch.distributed (default for N>1) or the C-ABI "
-                         "entries of include/m17gpu.h on an ncclComm_t; given explicitly the legs also run at N=1 (degenerate: "
-                         "device copies, every call made)")
+                    help="transport of the fan-out legs: m17_sdr_amd/shard.py over torch.distributed (default for N>1 with --full) or "
+                         "the C-ABI entries of include/m17gpu.h on an ncclComm_t; given explicitly the legs run without --full and also "
+                         "at N=1 (degenerate: device copies, every call made)")
     ap.add_argument("--no-syms", action="store_true", help="front end: do not write the symbol stream")
     ap.add_argument("--no-settle", action="store_true",
                     help="skip the untimed clock-settling calls in front of the warm-up steps (the timed region then sees the DVFS ramp)")
@@ -147,7 +158,7 @@ def launch_ranks(args, timeout_s=1200.0):
 # ------------------------------------------------------------------------------------------------
 # one rank
 # ------------------------------------------------------------------------------------------------
-def make_input(args, rank, torch, rx, C, nblk, T):
+def make_input(args, rank, torch, rx, C, nblk, T, want_host):
     """Synthetic IQ for this rank's channel shard, resident in HBM before the timed region.
     Default: ONE continuous signal per channel made on the device by m17gpu_gen_batch (SURVEY 8f-1,
     every channel distinct, seeded by global channel id: carrier, preambles, link setup frame, 40
@@ -155,7 +166,8 @@ def make_input(args, rank, torch, rx, C, nblk, T):
     nblk x 40 ms of every channel, as a live receiver would.  At most --signal-gb of distinct signal is
     kept; longer runs wrap around (one frame-phase break per pass, like a transmission cut short).
     --gen host: the host generator, tiled to C channels, the same slab every step.
-    Returns (list of per-step device tensors, host copy of <= 256 channels of the first timed slab)."""
+    Returns (list of per-step device tensors, host copy of >= 256 channels of the first timed slab for the
+    CPU baseline -- None from the device generator unless want_host --, number of distinct slabs)."""
     import m17_sdr_amd as m
     if args.gen == "gpu":
         Tg = max(1, min(T, int(args.signal_gb * 1e9 // (C * nblk * 7680))))
@@ -170,6 +182,8 @@ def make_input(args, rank, torch, rx, C, nblk, T):
         torch.cuda.synchronize(rx.device)
         torch.cuda.empty_cache()
         steps = [slabs[k % Tg] for k in range(T)]
+        if not want_host:
+            return steps, None, Tg
         w = min(args.warmup, Tg - 1)
         nhost = min(C, max(256, 4 * host_cores()[0]))          # cpu_baseline: >= 4 channels per usable host thread
         return steps, {"iq": steps[w][:nhost].cpu().numpy()}, Tg
@@ -753,6 +767,36 @@ def fanout_legs(args, torch, dist, rx, out, iq_step, world, rank, backend, C, nb
                           else f"m17_sdr_amd.shard over torch.distributed: {backend} (rehearsal, staged through host)")}
 
 
+def dump_outputs(dirname, counts, recs, syms=None, nsyms=None, budget=DUMP_BUDGET):
+    """Write what one m17gpu_rx_blocks call returned -- host copies: counts [C], recs [C, rec_cap, 64] uint8, optionally
+    syms [C, stride] / nsyms [C, nblk] -- as dirname/<name>.npy, every value exact in float32 / float64, so that two builds
+    can be compared output for output.  Records: the valid rows only (min(count, rec_cap) per channel, channel-major), one
+    file per field, `rec_data` the 32 payload bytes as eight little-endian uint32 words; symbols: each channel's valid
+    prefix (sum of its nsyms), concatenated.  When every slot of every channel would exceed `budget` bytes, a seeded sample
+    of channels, fixed by the shapes alone, is written; `channels` names the channels written.  Returns the bytes written."""
+    import m17_sdr_amd as m
+    C, cap = recs.shape[:2]
+    per_channel = 16 + cap * (7 * 4 + 8 + 4 + 8 * 8) + (0 if syms is None else 4 * (syms.shape[1] + nsyms.shape[1]))
+    k = min(C, budget // per_channel)
+    chans = np.arange(C) if k == C else np.sort(np.random.default_rng(DUMP_SEED).choice(C, k, replace=False))
+    counts = counts[chans]
+    rec = np.ascontiguousarray(recs[chans]).view(np.dtype(m.Rec))[..., 0]
+    rec = rec[np.arange(cap)[None, :] < np.minimum(counts, cap)[:, None]]
+    arrays = {"channels": chans.astype(np.float64), "counts": counts.astype(np.float64)}
+    for f in ("type", "votes", "golay_errs", "frame_errors", "flags", "fn", "sym_pos", "variance"):
+        arrays["rec_" + f] = rec[f].astype(np.float32)
+    arrays["rec_block"] = rec["block"].astype(np.float64)
+    arrays["rec_data"] = np.ascontiguousarray(rec["data"]).view("<u4").astype(np.float64)
+    if syms is not None:
+        ns, s = nsyms[chans], syms[chans]
+        arrays["nsyms"] = ns.astype(np.float32)
+        arrays["syms"] = s[np.arange(s.shape[1])[None, :] < ns.sum(axis=1)[:, None]].astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def run_rank(args):
     import torch
     import torch.distributed as dist
@@ -784,7 +828,8 @@ def run_rank(args):
     for kv in args.option:
         name, value = kv.split("=")
         rx.set_option(name, int(value))
-    iq, sig, Tg = make_input(args, rank, torch, rx, C, nblk, T)
+    cpu_base = args.full and not args.no_cpu_baseline and world == 1
+    iq, sig, Tg = make_input(args, rank, torch, rx, C, nblk, T, want_host=cpu_base)
     out = rx.alloc_outputs(nblk, want_syms=(mode == 0 and not args.no_syms))
 
     def barrier():
@@ -796,6 +841,9 @@ def run_rank(args):
     settled = 0
     if not args.no_settle:
         settled = settle(torch, local, rx, iq[:Tg], mode, out)
+        # the number of settle calls follows the clock; the receiver's state (block counter, timing loop, framer) must not,
+        # so that the steps below compute the same on every run
+        rx.reset()
     for k in range(args.warmup):
         rx.rx_blocks(iq[k], mode, out)
     barrier()
@@ -808,6 +856,9 @@ def run_rank(args):
     rx.set_profiling(False)
     kms, ncalls = rx.kernel_ms()
     path = rx.last_path()
+    if args.dump_outputs and rank == 0:
+        host = {k: (None if out[k] is None else out[k].cpu().numpy()) for k in ("counts", "recs", "syms", "nsyms")}
+        dump_outputs(args.dump_outputs, host["counts"], host["recs"], host["syms"], host["nsyms"])
 
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
@@ -841,7 +892,8 @@ def run_rank(args):
                    "ebn0_db": args.ebn0,
                    "settle_calls": settled,
                    "settle_note": "untimed conditioning in front of the warm-up steps: the same step back to back for ~0.4 s, so that the "
-                                  "shader clock has followed the load (DESIGN.md section 6; --no-settle to measure the ramp instead)",
+                                  "shader clock has followed the load, then a receiver reset, so that the steps compute the same on every "
+                                  "run (DESIGN.md section 6; --no-settle to measure the ramp instead)",
                    "signal_source": ("m17gpu_gen_batch (device), one continuous stream per channel, %d distinct steps "
                                      "(%.1f s) cut into %d-block steps%s" % (Tg, 0.04 * nblk * Tg, nblk, ", wrapping" if Tg < T else "")
                                      if args.gen == "gpu" else "m17gen_batch (host, tiled), the same slab every step"),
@@ -859,11 +911,11 @@ def run_rank(args):
     }
     if args.option:
         line["config"]["options"] = list(args.option)
-    if (world > 1 or args.fanout) and not args.no_fanout:
+    if ((world > 1 and args.full) or args.fanout) and not args.no_fanout:
         # After the timed region and outside `value`: neither a failure nor a HANG of the transfer legs may cost the
         # measurement.  A collective that never returns cannot be cancelled, so a watchdog prints the line as it stands
         # (rank 0) -- with whatever legs have finished -- and ends the process on every rank when a set of legs overruns
-        # its allowance.  N > 1 without --fanout runs BOTH bindings one after the other: the torch.distributed one
+        # its allowance.  N > 1 with --full and without --fanout runs BOTH bindings one after the other: the torch.distributed one
         # (rehearsed over gloo with two ranks) first, then the C-ABI entries on their own communicator (rehearsed with
         # one rank only: no multi-GPU box so far), so that a node that has the GPUs exercises both.
         import threading
@@ -908,18 +960,19 @@ def run_rank(args):
         rx.close()
         del iq
         torch.cuda.empty_cache()
-        if world == 1 and not args.no_noisy and mode == 1 and args.ebn0 >= 100.0:
+        legs = args.full and world == 1 and mode == 1
+        if legs and not args.no_noisy and args.ebn0 >= 100.0:
             line["noisy"] = noisy_leg(args, torch, local, C, nblk)
-        if world == 1 and not args.no_step12 and mode == 1 and (C, nblk) == (16384, 16) and args.ebn0 >= 100.0:
+        if legs and not args.no_step12 and (C, nblk) == (16384, 16) and args.ebn0 >= 100.0:
             line["step_12_blocks"] = step12_leg(args, torch, local, C)
-        if world == 1 and not args.no_step12 and mode == 1 and (C, nblk) == (16384, 16) and args.ebn0 >= 100.0:
+        if legs and not args.no_step12 and (C, nblk) == (16384, 16) and args.ebn0 >= 100.0:
             line["two_contexts"] = two_contexts_leg(args, torch, local, C, nblk)
-        if world == 1 and not args.no_fir_stage and mode == 1:
+        if legs and not args.no_fir_stage:
             line["fir_stage"] = fir_stage(args, torch, local)
             line["fir_stage_16384"] = fir_stage(args, torch, local, C=16384, nblk=16, steps=20, warm=3)
             line["fir_stage_16384x12"] = fir_stage(args, torch, local, C=16384, nblk=12, steps=20, warm=3)
             line["fir_stage_16384x48"] = fir_stage(args, torch, local, C=16384, nblk=48, steps=8, warm=2)
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_base:
             line["cpu_baseline"] = cpu_baseline(mode, sig)
         else:
             line["cpu_baseline"] = None

@@ -28,5 +28,5 @@ for wl in full full_12 frontend frontend_16384x16 frontend_16384x12 frontend_163
   echo "collected $wl"
 done
 cd $R
-python3 bench.py > $O/bench_full.json 2> $O/bench_full.err
+python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.err
 echo done

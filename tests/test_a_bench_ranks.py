@@ -15,14 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_starts_its_own_ranks_gloo_rehearsal():
-    """`python bench.py --gpus 2` must start two ranks itself (no torchrun) and report n_gpus == 2, with the
+    """`python bench.py --gpus 2 --full` must start two ranks itself (no torchrun) and report n_gpus == 2, with the
     fan-out legs (shard.scatter_iq -> compute -> shard.gather_records) timed apart.  On a 1-GPU box the two
     ranks share the card and the collectives run over gloo (M17_BENCH_BACKEND=gloo); on a multi-GPU node
     the same code path runs one rank per GPU over RCCL."""
     env = dict(os.environ, M17_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--channels", "96", "--blocks", "6", "--no-cpu-baseline", "--no-noisy"],
+                        "--channels", "96", "--blocks", "6", "--full", "--no-cpu-baseline", "--no-noisy"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -71,7 +71,7 @@ def test_bench_line_survives_a_failing_fanout_leg():
     env = dict(os.environ, M17_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4", M17_BENCH_INJECT_FANOUT_FAILURE="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--channels", "64", "--blocks", "4", "--no-cpu-baseline", "--no-noisy"],
+                        "--channels", "64", "--blocks", "4", "--full", "--no-cpu-baseline", "--no-noisy"],
                        env=env, capture_output=True, text=True, timeout=150)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -87,7 +87,7 @@ def test_bench_line_survives_a_hanging_fanout_leg():
                M17_BENCH_FANOUT_TIMEOUT="8")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--channels", "64", "--blocks", "4", "--no-cpu-baseline", "--no-noisy"],
+                        "--channels", "64", "--blocks", "4", "--full", "--no-cpu-baseline", "--no-noisy"],
                        env=env, capture_output=True, text=True, timeout=150)
     assert r.returncode == 3, (r.returncode, r.stdout[-2000:] + r.stderr[-2000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
