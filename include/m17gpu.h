@@ -49,6 +49,7 @@ extern "C" {
 #define M17GPU_F_LSF_GATE   0x0040  /* decode_link_frame's CRC gate   (m17_rx_parse.cpp:98, quirk H9) */
 #define M17GPU_F_PKT_VALID  0x0080  /* parse_packet CRC==0 at EOF     (m17_rx_parse.cpp:42-45) */
 #define M17GPU_F_AOS        0x0100  /* lock acquired, not a frame     (m17_rx_frame.cpp:165-169) */
+#define M17GPU_F_BERT_SYNC  0x0200  /* BERT frame ("bert" option): the PRBS9 checker is in sync after its last bit */
 
 /* One 64-byte record per framer event of one channel, in event order.
  * It carries what the reference hands to its sinks (m17_net_new_rx_data
@@ -64,7 +65,9 @@ typedef struct {
     uint32_t block;         /* 1920-sample block index since reset */
     uint16_t sym_pos;       /* index of the completing symbol inside that block */
     uint16_t rsv0;
-    uint8_t  data[32];      /* LSF: 30 B | stream: LICH chunk[6] + FN/payload[18] | packet: 26 B */
+    uint8_t  data[32];      /* LSF: 30 B | stream: LICH chunk[6] + FN/payload[18] | packet: 26 B |
+                               BERT ("bert" option): 197 bits in data[0..24] MSB first, data[25] bits checked in sync,
+                               data[26] errors among them */
     uint8_t  rsv[12];
 } m17gpu_rec;
 
@@ -135,9 +138,16 @@ int m17gpu_viterbi_decode(m17gpu_ctx *ctx, const float *d_soft, uint8_t *d_bits,
 /* m17_dsp_demap_frame (m17_dsp.cpp:82-95): d_sym [n][192] -> d_soft [n][368] */
 int m17gpu_demap_frame(m17gpu_ctx *ctx, const float *d_sym, float *d_soft, int n, void *stream);
 /* stateless part of m17_rx_parse (m17_rx_parse.cpp:86-177): frame symbols
- * d_sym [n][192] + d_type [n] -> data/fn/golay_errs of d_recs [n]; no LICH state. */
+ * d_sym [n][192] + d_type [n] -> data/fn/golay_errs of d_recs [n]; no LICH state.
+ * With the "bert" option BERT frames (type 4) are decoded too: data[0..24] = the 197 bits (the PRBS9 checker
+ * is not run; data[25..31] stay 0). */
 int m17gpu_decode_frames(m17gpu_ctx *ctx, const float *d_sym, const uint8_t *d_type,
                          m17gpu_rec *d_recs, int n, void *stream);
+/* The PRBS9 checker of the "bert" option on a host's own frame streams (a host with its own framer, and tests):
+ * per channel n entries in order, d_kind [C][n] = 0 decoded BERT frame (its 197 bits in d_bits [C][n][25], MSB
+ * first), 1 erased BERT frame (a parsed record of another type), 2 AOS.  d_out [C][n][2] = bits checked in sync,
+ * errors among them.  The same device code and the same per-channel state as the full chain. */
+int m17gpu_bert_feed(m17gpu_ctx *ctx, const uint8_t *d_bits, const uint8_t *d_kind, int n, uint8_t *d_out, void *stream);
 /* m_17_golay_decode (m17_golay.cpp:103-116) on n 24-bit words: d_out[i] = data | weight<<12 */
 int m17gpu_golay_decode(m17gpu_ctx *ctx, const uint32_t *d_words, uint16_t *d_out, int n, void *stream);
 
@@ -168,7 +178,15 @@ int m17gpu_golay_decode(m17gpu_ctx *ctx, const uint32_t *d_words, uint16_t *d_ou
  *   "book_impl"          the bookkeeping kernel: 0 = by batch (default): a lane per channel (k_book_lanes) from 8,192 channels
  *                            on, a wave per channel (k_book_chan) below and whenever the network sink is attached; 1 / 2 force
  *                            the wave / the lane kernel (2 still yields to the network sink)
- * and one functional switch:
+ * and two functional switches:
+ *   "bert"               0 (default) | 1 = BERT receive, which the reference leaves empty (decode_bert_frame,
+ *                            m17_rx_parse.cpp:178-180).  A parsed BERT frame is decoded as the inverse of
+ *                            m17_fmt_add_bert_frame (demap, de-randomise, de-interleave, one erasure as soft bit 368 for
+ *                            the coded bit that is never sent, P2 de-puncture to 402, Viterbi, bits[1..197]) and fed to the
+ *                            PRBS9 checker of m17_prbs9.cpp:40-64 with its quirks; an AOS record resets the checker, any
+ *                            other parsed record while in sync advances it by one frame (an erased BERT frame).  Results:
+ *                            data[25], data[26] and M17GPU_F_BERT_SYNC of each BERT record, m17gpu_get_bert.  At 0
+ *                            records, counters and launches are those of a build without it.
  *   "afc"                0 (default, as the reference ships: radio.cpp:8) | 1 = radio_set_afc_on(): the
  *                            NCO mixer of m17_dsp.cpp:390-408,468 with the loop of radio.cpp:196-208 per channel.
  *                            The correction closes a loop over the whole chain, so an AFC context is processed
@@ -196,6 +214,12 @@ int m17gpu_get_call_ms(m17gpu_ctx *ctx, float h_ms[4], float *h_call_ms, int *h_
 int m17gpu_selftest(m17gpu_ctx *ctx, unsigned *h_bad);
 
 /* ---------------- state access (host, synchronous) ---------------- */
+/* the PRBS9 checkers of the "bert" option (either pointer may be NULL):
+ * h_cnt [C][6]   = bits checked in sync, errors among them, BERT frames decoded, frames erased, locks, losses
+ *                  (a loss: 18 mismatches in a row; an AOS reset is not one);
+ * h_state [C][6] = m_rx_idx, m_rx_state (0 NO_SYNC, 1 IN_SYNC), m_rx_bad, m_rx_good, m_rx_eq_cnt, m_rx_dif_cnt
+ *                  (m17_prbs9.cpp:6-12).  m17gpu_create / m17gpu_reset zero them all. */
+int m17gpu_get_bert(m17gpu_ctx *ctx, uint64_t *h_cnt, int32_t *h_state);
 /* the reassembled LSF pair m_lsf[2][30] of each channel (m17_rx_parse.cpp:5) */
 int m17gpu_get_lsf(m17gpu_ctx *ctx, uint8_t *h_lsf /* [C][2][30] */);
 /* g_errors, n_frames, in_frame, frame_id_epoch per channel (m17_dbase.cpp:60-82) */
@@ -356,6 +380,14 @@ int m17gen_build_lsf(uint64_t dst, uint64_t src, uint16_t type_word, const uint8
 uint64_t m17gen_encode_call(const char *call9);
 /* modulate n dibits (value 0..3, or 255 = zero deviation) appending 10 samples each */
 int m17gen_modulate(const uint8_t *dibits, int n, int16_t *h_iq, int reset);
+/* m17_fmt_add_bert_frame (m17_tx_routines.cpp:226-238): the next 197 PRBS9 bits from *prbs_idx (advanced, mod 511),
+ * 4-bit zero tail, rate-1/2 code, P2 (the first 368 of 369 bits), interleave, randomise, sync 0xDF55 */
+int m17gen_bert_frame_dibits(uint16_t *prbs_idx, uint8_t dibits[192]);
+/* BERT transmissions on C channels: carrier, preamble, n_bert_frames BERT frames (PRBS from index 0, running on across
+ * the frames), EOT, repeated until nblk blocks are filled; per-channel delay and noise as m17gen_batch.
+ * h_iq [C][nblk][1920][2]; h_nframes [C] (optional) = BERT frames started. */
+int m17gen_bert_batch(int C, uint64_t base_seed, int first_channel, int nblk, int n_bert_frames,
+                      float ebn0_db, float noise_cutoff_hz, int16_t *h_iq, int32_t *h_nframes, int nthreads);
 
 /* GPU-side signal source: the signal of m17gen_batch (stream mode) for the
  * context's C channels, made on the device: d_iq [C][nblk][1920][2] int16; optional d_lsf

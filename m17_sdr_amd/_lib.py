@@ -18,6 +18,7 @@ SOFT_BITS = 368
 
 F_SYNC_OK, F_PARSED, F_LICH_OK, F_DELIVERED = 0x1, 0x2, 0x4, 0x8
 F_EOT, F_LOST, F_LSF_GATE, F_PKT_VALID, F_AOS = 0x10, 0x20, 0x40, 0x80, 0x100
+F_BERT_SYNC = 0x200
 OK, ERR_NO_DEVICE, ERR_HIP, ERR_ARG, ERR_NOMEM = 0, -1, -2, -3, -4      # M17GPU_* status codes
 
 
@@ -56,6 +57,8 @@ SIGNATURES = {
     "m17gpu_demap_frame": (_i, [_vp, _vp, _vp, _i, _vp]),
     "m17gpu_decode_frames": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "m17gpu_golay_decode": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "m17gpu_bert_feed": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "m17gpu_get_bert": (_i, [_vp, _vp, _vp]),
     "m17gpu_set_option": (_i, [_vp, C.c_char_p, _i]),
     "m17gpu_set_profiling": (_i, [_vp, _i]),
     "m17gpu_get_kernel_ms": (_i, [_vp, _vp, _vp]),
@@ -89,6 +92,8 @@ SIGNATURES = {
     "m17gen_build_lsf": (_i, [_u64, _u64, C.c_uint16, _vp, _vp]),
     "m17gen_encode_call": (_u64, [C.c_char_p]),
     "m17gen_modulate": (_i, [_vp, _i, _vp, _i]),
+    "m17gen_bert_frame_dibits": (_i, [_vp, _vp]),
+    "m17gen_bert_batch": (_i, [_i, _u64, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _i]),
     "m17gpu_gen_batch": (_i, [_vp, _u64, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _i, _vp, _vp]),
     "m17gpu_gen_batch_stages": (_i, [_vp, _u64, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
 }

@@ -210,6 +210,18 @@ class Receiver:
                "m17gpu_decode_frames")
         return recs
 
+    def bert_feed(self, bits, kinds):
+        """The PRBS9 checker of the "bert" option on the caller's streams (m17gpu_bert_feed): bits uint8 [C, n, 25] (197
+        bits each, MSB first), kinds uint8 [C, n] (0 decoded frame, 1 erased frame, 2 AOS), cuda tensors.  Returns uint8
+        [C, n, 2]: bits checked in sync, errors among them.  Carries the same checker state as the full chain."""
+        import torch
+        n = int(kinds.shape[1]) if kinds.dim() == 2 else -1
+        self._chk(kinds, torch.uint8, (self.C, n), "kinds")
+        self._chk(bits, torch.uint8, (self.C, n, 25), "bits")
+        out = torch.zeros((self.C, n, 2), dtype=torch.uint8, device=kinds.device)
+        _check(lib().m17gpu_bert_feed(self._ctx, _ptr(bits), _ptr(kinds), n, _ptr(out), self._stream()), "m17gpu_bert_feed")
+        return out
+
     def golay_decode(self, words):
         import torch
         n = int(words.shape[0])
@@ -340,6 +352,16 @@ class Receiver:
         _check(lib().m17gpu_get_last_path(self._ctx, a), "m17gpu_get_last_path")
         return {"fir": a[0], "plain_slots": a[1], "book": a[2]}
 
+    def bert(self):
+        """The PRBS9 checkers of the "bert" option (m17gpu_get_bert): dict of numpy arrays [C] -- bits (checked in sync),
+        errors, frames, erased, locks, losses (uint64) and idx, state, bad, good, eq_cnt, dif_cnt (the reference's m_rx_*)."""
+        cnt = np.zeros((self.C, 6), np.uint64)
+        stt = np.zeros((self.C, 6), np.int32)
+        _check(lib().m17gpu_get_bert(self._ctx, cnt.ctypes.data_as(C.c_void_p), stt.ctypes.data_as(C.c_void_p)), "m17gpu_get_bert")
+        out = {k: cnt[:, i].copy() for i, k in enumerate(("bits", "errors", "frames", "erased", "locks", "losses"))}
+        out.update({k: stt[:, i].copy() for i, k in enumerate(("idx", "state", "bad", "good", "eq_cnt", "dif_cnt"))})
+        return out
+
     def lock(self):
         a = np.zeros((self.C,), np.uint8)
         _check(lib().m17gpu_get_lock(self._ctx, a.ctypes.data_as(C.c_void_p)), "m17gpu_get_lock")
@@ -376,3 +398,16 @@ def generate_batch(n_channels, nblk, n_stream_frames=40, ebn0_db=200.0, base_see
     if rc != 0:
         raise RuntimeError(f"m17gen_batch failed ({rc})")
     return {"iq": iq, "lsf": lsf, "payload": pl, "nframes": nf}
+
+
+def generate_bert_batch(n_channels, nblk, n_bert_frames=40, ebn0_db=200.0, base_seed=0x4D313700, first_channel=0,
+                        nthreads=8, noise_cutoff_hz=0.0):
+    """Host signal source of BERT transmissions (m17gen_bert_batch): carrier, preamble, n_bert_frames BERT frames (PRBS9
+    from index 0), EOT, repeated.  Returns dict(iq[C,nblk,1920,2] int16, nframes[C])."""
+    iq = np.zeros((n_channels, nblk, 1920, 2), np.int16)
+    nf = np.zeros((n_channels,), np.int32)
+    rc = lib().m17gen_bert_batch(n_channels, base_seed, first_channel, nblk, n_bert_frames, ebn0_db, noise_cutoff_hz,
+                                 iq.ctypes.data_as(C.c_void_p), nf.ctypes.data_as(C.c_void_p), nthreads)
+    if rc != 0:
+        raise RuntimeError(f"m17gen_bert_batch failed ({rc})")
+    return {"iq": iq, "nframes": nf}

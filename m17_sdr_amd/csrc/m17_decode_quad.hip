@@ -31,6 +31,7 @@ constexpr int DQ_NPER   = DQ_CHUNK / 2;        // soft bits per lane and chunk
 constexpr int DQ_RING   = 2 * DQ_CHUNK;
 constexpr int DQ_DECW   = 31;                  // ceil(244 / 8) decision rows: any frame type
 constexpr int DQ_DECW_STREAM = 19;             // ceil(148 / 8): stream frames
+constexpr int DQ_DECW_BERT = 26;               // ceil(202 / 8): BERT frames (201 steps, the forward pass runs an even 202)
 
 // Per-frame LDS.  The record payload bytes are assembled after the forward pass, in the ring's place.
 // DECW = 31: 624 B = 4 x 39 dwords, DECW = 19: 432 B = 4 x 27 dwords -- either way the 16 frames of a wave
@@ -105,12 +106,14 @@ __host__ __device__ inline DqLich dq_lich_entry(int g)       // e: offset, bit 1
 
 // 1,024 threads per workgroup and one atomic per (workgroup, type): all waves appending to
 // the same counter serialise in L2 (measured 40 us for 1,660 wave-level atomics).
+// maxtype 3: link-setup, stream and packet frames (lists 0..2); 4 (the "bert" option): BERT frames too, on list 3.
 __global__ __launch_bounds__(1024)
 void k_worklist(const m17gpu_rec_dev *__restrict__ recs, int rec_cap, const int32_t *__restrict__ counts, int C,
-                int32_t *__restrict__ work, int32_t *__restrict__ nwork, int cap)
+                int32_t *__restrict__ work, int32_t *__restrict__ nwork, int cap, int maxtype, int32_t *__restrict__ clear_word)
 {
-    __shared__ int wcount[3][16];                 // [type][wave]
-    __shared__ int wbase[3][16];
+    if (clear_word && blockIdx.x == 0 && threadIdx.x == 0) *clear_word = 0;     // ("bert" option: k_bert_chain's away_out)
+    __shared__ int wcount[4][16];                 // [type][wave]
+    __shared__ int wbase[4][16];
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const int chan = (int)(i / rec_cap), r = (int)(i - (long long)chan * rec_cap);
@@ -118,17 +121,17 @@ void k_worklist(const m17gpu_rec_dev *__restrict__ recs, int rec_cap, const int3
     if (chan < C && r < min(counts[chan], rec_cap)) {
         const uint32_t *w = reinterpret_cast<const uint32_t *>(&recs[i]);
         const uint32_t w0 = w[0], w1 = w[1];
-        if ((w1 & M17_F_PARSED) && (w0 & 0xFF) >= 1 && (w0 & 0xFF) <= 3) ty = (int)(w0 & 0xFF);
+        if ((w1 & M17_F_PARSED) && (w0 & 0xFF) >= 1 && (int)(w0 & 0xFF) <= maxtype) ty = (int)(w0 & 0xFF);
     }
     const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned long long m[3];
+    unsigned long long m[4];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 4; ++k) {
         m[k] = __ballot(ty == k + 1);
         if (lane == 0) wcount[k][wave] = (int)__popcll(m[k]);
     }
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if ((int)threadIdx.x < maxtype) {
         const int k = (int)threadIdx.x;
         int tot = 0;
         for (int w = 0; w < 16; ++w) { wbase[k][w] = tot; tot += wcount[k][w]; }
@@ -162,9 +165,13 @@ __device__ __forceinline__ void decode_quad_pass(QuadFrameT<DECW, NSYM> &F, cons
                                                  const float *__restrict__ gs_next, dq_f4 (&pre)[NSYM ? NSYM / 16 : 1])
 {
     const int type = TYPE_CT ? TYPE_CT : type_rt;
-    const int steps = (type == 1) ? 244 : (type == 2 ? 148 : 210);       // DevTables.glen / 2
-    const int nbits = (type == 1) ? 240 : (type == 2 ? 144 : 208);
+    const int steps = (type == 1) ? 244 : (type == 2 ? 148 : (type == 4 ? 201 : 210));       // DevTables.glen / 2
+    const int nbits = (type == 1) ? 240 : (type == 2 ? 144 : (type == 4 ? 197 : 208));
     const int boff = (type == 2) ? 6 : 0;
+    // The forward pass goes two steps at a time.  A BERT frame has 201: its pass runs a 202nd on two erasures (the table
+    // row is padded with them) whose decisions the traceback never reads -- it starts from state 0 after step 200, as
+    // m17_viterbi_decode does (m17_conv.cpp:160), and metrics up to step 200 do not depend on what follows.
+    const int fsteps = (steps + 1) & ~1;
     // soft bits of steps c0 .. c0+31 (row padded with erasures).  Plain 192-symbol frames (TYPE_CT == 0): quad lane j
     // makes ring[j], ring[j+4], ..., each from a gather through the table.  Regrouped stream slots (TYPE_CT == 2,
     // m17_dev.h kSlotFloats): lane j makes ring[16j .. 16j+15] from 64 contiguous bytes of the slot.
@@ -307,10 +314,10 @@ __device__ __forceinline__ void decode_quad_pass(QuadFrameT<DECW, NSYM> &F, cons
     commit_chunk(0);
     wave_fence();
     asm volatile("s_nop 1");
-    for (int c0 = 0; c0 < steps; c0 += DQ_CHUNK) {
-        if (c0 + DQ_CHUNK < steps) fetch_chunk(c0 + DQ_CHUNK);       // in flight during this chunk's butterflies
+    for (int c0 = 0; c0 < fsteps; c0 += DQ_CHUNK) {
+        if (c0 + DQ_CHUNK < fsteps) fetch_chunk(c0 + DQ_CHUNK);       // in flight during this chunk's butterflies
         STAMP(2);
-        const int tend2 = min(DQ_CHUNK, steps - c0) >> 1;     // steps is even
+        const int tend2 = min(DQ_CHUNK, fsteps - c0) >> 1;
         const float4 *ring4 = reinterpret_cast<const float4 *>(F.ring);
         float4 cur = ring4[0];
         for (int t2 = 0; t2 < tend2; ++t2) {
@@ -332,7 +339,7 @@ __device__ __forceinline__ void decode_quad_pass(QuadFrameT<DECW, NSYM> &F, cons
                 for (int r = 0; r < NSYM / 16; ++r) pre[r] = g4[r];
             }
         }
-        if (c0 + DQ_CHUNK < steps) { commit_chunk(c0 + DQ_CHUNK); wave_fence(); }
+        if (c0 + DQ_CHUNK < fsteps) { commit_chunk(c0 + DQ_CHUNK); wave_fence(); }
         STAMP(3);
     }
     // the ring has been read for the last time: its place becomes the record payload
@@ -404,18 +411,20 @@ __device__ __forceinline__ void decode_quad_pass(QuadFrameT<DECW, NSYM> &F, cons
 
 // Workgroup-shared storage of the decoder for WAVES waves, each on its own 16 frames.
 // ONLY == 2: stream frames only: per-frame LDS sized for 148 trellis steps, one shared table row.
+// ONLY == 4: BERT frames only (the "bert" option): sized for 202 steps, one shared table row.
 // ONLY == 0: any frame type, a table row per wave.
+template <int ONLY> constexpr int dq_decw() { return ONLY == 2 ? DQ_DECW_STREAM : (ONLY == 4 ? DQ_DECW_BERT : DQ_DECW); }
 template <int ONLY, int WAVES, int NSYM = 0>
 struct alignas(16) DqShared {
-    QuadFrameT<(ONLY == 2) ? DQ_DECW_STREAM : DQ_DECW, NSYM> fr[WAVES][DQ_FRAMES];   // 7 KB (stream; 19 KB with symbol staging) / 10 KB per wave
+    QuadFrameT<dq_decw<ONLY>(), NSYM> fr[WAVES][DQ_FRAMES];   // 7 KB (stream; 19 KB with symbol staging) / 10 KB per wave
     uint32_t gt_rows[ONLY ? 1 : WAVES][512];                                   // DevTables.gather row of the current type, re-coded
     DqLich   lich_row[96];
 };
 
 // The decoder as workgroup number wg of n_wg workgroups of WAVES waves (threads beyond 64 * WAVES must not enter).
-// work != nullptr: lists per type (work[3][cap], nwork[3]; ONLY == 2 takes the stream list, ONLY == 0 all of them or,
-// with skip_stream, all but the stream list); else (ONLY == 0) plain batch: frame i of n_plain, type from types[i],
-// record i.
+// work != nullptr: lists per type (work[4][cap], nwork[4]; ONLY == 2 takes the stream list, ONLY == 4 the BERT list,
+// ONLY == 0 the link-setup, stream and packet lists or, with skip_stream, all but the stream list); else (ONLY == 0)
+// plain batch: frame i of n_plain, type from types[i], record i -- BERT frames (type 4) too when `bert` is set.
 template <int ONLY, int WAVES, int NSYM = 0>
 __device__ __forceinline__ void decode_quad_body(DqShared<ONLY, WAVES, NSYM> &sh, int wg, int n_wg,
                    const float *__restrict__ fsym, const int32_t *__restrict__ work,
@@ -423,9 +432,9 @@ __device__ __forceinline__ void decode_quad_body(DqShared<ONLY, WAVES, NSYM> &sh
                    const uint8_t *__restrict__ types, int n_plain,
                    m17gpu_rec_dev *__restrict__ recs,
                    const uint16_t *__restrict__ genc, const uint16_t *__restrict__ gerr, int skip_stream,
-                   int slot_floats, bool spectator = false)
+                   int slot_floats, bool spectator = false, int bert = 0)
 {
-    using Frame = QuadFrameT<(ONLY == 2) ? DQ_DECW_STREAM : DQ_DECW, NSYM>;
+    using Frame = QuadFrameT<dq_decw<ONLY>(), NSYM>;
     const int lane = lane_id(), q = lane >> 2, j = lane & 3, wave = (int)(threadIdx.x >> 6);
     Frame &F = sh.fr[wave][q];
     uint32_t *gt_row = sh.gt_rows[ONLY ? 0 : wave];
@@ -446,7 +455,7 @@ __device__ __forceinline__ void decode_quad_body(DqShared<ONLY, WAVES, NSYM> &sh
     // before the tables are filled -- the any-type kernel normally finds its lists empty
     {
         int m1 = 0, m2 = 0, m3 = 0;
-        if (work) { m1 = min(nwork[0], cap); m2 = min(nwork[1], cap); m3 = min(nwork[2], cap); }
+        if (work) { m1 = min(nwork[0], cap); m2 = min(nwork[ONLY == 4 ? 3 : 1], cap); m3 = min(nwork[2], cap); }
         if (ONLY == 0 && skip_stream) m2 = 0;
         const int tasks = ONLY ? (m2 + DQ_FRAMES - 1) / DQ_FRAMES
                                : (work ? (m1 + DQ_FRAMES - 1) / DQ_FRAMES + (m2 + DQ_FRAMES - 1) / DQ_FRAMES + (m3 + DQ_FRAMES - 1) / DQ_FRAMES
@@ -465,8 +474,9 @@ __device__ __forceinline__ void decode_quad_body(DqShared<ONLY, WAVES, NSYM> &sh
     }
     __syncthreads();                                                        // the only workgroup barrier: tables are read-only from here
 
+    // (n2 / t2: the role's own list -- stream frames, or BERT frames for ONLY == 4)
     int n1 = 0, n2 = 0, n3 = 0;
-    if (work) { n1 = min(nwork[0], cap); n2 = min(nwork[1], cap); n3 = min(nwork[2], cap); }     // a list never holds more than its capacity (k_worklist)
+    if (work) { n1 = min(nwork[0], cap); n2 = min(nwork[ONLY == 4 ? 3 : 1], cap); n3 = min(nwork[2], cap); }     // a list never holds more than its capacity (k_worklist)
     if (ONLY == 0 && skip_stream) n2 = 0;
     const int t2 = (n2 + DQ_FRAMES - 1) / DQ_FRAMES, t1 = (n1 + DQ_FRAMES - 1) / DQ_FRAMES,
               t3 = (n3 + DQ_FRAMES - 1) / DQ_FRAMES;
@@ -476,7 +486,7 @@ __device__ __forceinline__ void decode_quad_body(DqShared<ONLY, WAVES, NSYM> &sh
     // the frame a quad works on in task `task` (work-list mode): list, index and whether it exists
     auto pick = [&](int task, int &qtype, bool &active) -> size_t {
         int seg, base, n;
-        if (ONLY || task < t2) { seg = 1; base = task * DQ_FRAMES; n = n2; }               // stream frames first
+        if (ONLY || task < t2) { seg = ONLY == 4 ? 3 : 1; base = task * DQ_FRAMES; n = n2; }  // stream frames first
         else if (task < t2 + t1) { seg = 0; base = (task - t2) * DQ_FRAMES; n = n1; }
         else { seg = 2; base = (task - t2 - t1) * DQ_FRAMES; n = n3; }
         active = base + q < n;
@@ -523,9 +533,10 @@ __device__ __forceinline__ void decode_quad_body(DqShared<ONLY, WAVES, NSYM> &sh
             decode_quad_pass<Frame::kDecw, ONLY, NSYM>(F, gs, gt_row, lich_row, ONLY, j, active, r0_keep, rec, C1, C2, genc, gerr, acc_, last_,
                                                        gs_next, pre);
         } else {
+            const int npass = (!work && bert) ? 4 : 3;
 #pragma unroll 1
-            for (int pass = 0; pass < 3; ++pass) {
-                const int type = (pass == 0) ? 2 : (pass == 1 ? 1 : 3);
+            for (int pass = 0; pass < npass; ++pass) {
+                const int type = (pass == 0) ? 2 : (pass == 1 ? 1 : (pass == 2 ? 3 : 4));
                 if (__ballot(qtype == type) == 0ull) continue;
                 if (row_type != type) {
                     for (int i = lane; i < 512; i += 64) gt_row[i] = dq_entry((i < 488) ? (int)c_tab.gather[type][i] : -1);
@@ -551,11 +562,11 @@ void k_decode_quad(const float *__restrict__ fsym, const int32_t *__restrict__ w
                    const uint8_t *__restrict__ types, int n_plain,
                    m17gpu_rec_dev *__restrict__ recs,
                    const uint16_t *__restrict__ genc, const uint16_t *__restrict__ gerr, int skip_stream,
-                   int slot_floats)
+                   int slot_floats, int bert)
 {
     __shared__ DqShared<ONLY, 4> sh;
     decode_quad_body<ONLY, 4>(sh, (int)blockIdx.x, (int)gridDim.x, fsym, work, nwork, cap, types, n_plain, recs, genc, gerr,
-                              skip_stream, slot_floats);
+                              skip_stream, slot_floats, false, bert);
 }
 
 // The work lists of one m17gpu_rx_blocks call in ONE launch.  Workgroups [0, n_other) take the link-setup and packet
@@ -564,18 +575,29 @@ void k_decode_quad(const float *__restrict__ fsym, const int32_t *__restrict__ w
 // launch of its own, behind the stream launch, that was 38 us added to every call; here it runs beside the stream
 // tasks.  The any-type workgroups come first so that they are placed at once; with their lists empty they leave
 // before touching their tables.
+// With the "bert" option the BERT list gets a role of its own, sized by the host like the stream role: workgroups
+// [n_other, n_other + n_bert), the trellis length a constant of the role.  Its frames need 560 B of LDS each (202 steps
+// of decisions), so three waves of them fit the stream role's 30.5 KB; the fourth wave only meets the barrier.
+// n_bert = 0 (option off): the launch is the one without the role.
+constexpr int DQ_BERT_WAVES = 3;
 __global__ __launch_bounds__(256, 5)
 void k_decode_lists(const float *__restrict__ fsym, const int32_t *__restrict__ work,
                     const int32_t *__restrict__ nwork, int cap, m17gpu_rec_dev *__restrict__ recs,
-                    const uint16_t *__restrict__ genc, const uint16_t *__restrict__ gerr, int slot_floats, int n_other)
+                    const uint16_t *__restrict__ genc, const uint16_t *__restrict__ gerr, int slot_floats, int n_other,
+                    int n_bert)
 {
-    __shared__ union U { DqShared<2, 4> s; DqShared<0, 2> o; __device__ U() {} } sh;
+    __shared__ union U { DqShared<2, 4> s; DqShared<0, 2> o; DqShared<4, DQ_BERT_WAVES> b; __device__ U() {} } sh;
     static_assert(sizeof(DqShared<0, 2>) <= sizeof(DqShared<2, 4>), "the any-type role must fit the stream role's LDS");
-    if ((int)blockIdx.x < n_other) {
-        decode_quad_body<0, 2>(sh.o, (int)blockIdx.x, n_other, fsym, work, nwork, cap, nullptr, 0, recs, genc, gerr, 1, slot_floats,
+    static_assert(sizeof(DqShared<4, DQ_BERT_WAVES>) <= sizeof(DqShared<2, 4>), "the BERT role must fit the stream role's LDS");
+    const int wg = (int)blockIdx.x;
+    if (wg < n_other) {
+        decode_quad_body<0, 2>(sh.o, wg, n_other, fsym, work, nwork, cap, nullptr, 0, recs, genc, gerr, 1, slot_floats,
                                threadIdx.x >= 128);
+    } else if (wg < n_other + n_bert) {
+        decode_quad_body<4, DQ_BERT_WAVES>(sh.b, wg - n_other, n_bert, fsym, work, nwork, cap, nullptr, 0, recs, genc, gerr, 0,
+                                           slot_floats, threadIdx.x >= 64 * DQ_BERT_WAVES);
     } else {
-        decode_quad_body<2, 4>(sh.s, (int)blockIdx.x - n_other, (int)gridDim.x - n_other, fsym, work, nwork, cap, nullptr, 0,
+        decode_quad_body<2, 4>(sh.s, wg - n_other - n_bert, (int)gridDim.x - n_other - n_bert, fsym, work, nwork, cap, nullptr, 0,
                                recs, genc, gerr, 0, slot_floats);
     }
 }
@@ -586,15 +608,21 @@ void k_decode_lists(const float *__restrict__ fsym, const int32_t *__restrict__ 
 __global__ __launch_bounds__(256, 2)
 void k_decode_lists_p(const float *__restrict__ fsym, const int32_t *__restrict__ work,
                       const int32_t *__restrict__ nwork, int cap, m17gpu_rec_dev *__restrict__ recs,
-                      const uint16_t *__restrict__ genc, const uint16_t *__restrict__ gerr, int slot_floats, int n_other)
+                      const uint16_t *__restrict__ genc, const uint16_t *__restrict__ gerr, int slot_floats, int n_other,
+                      int n_bert)
 {
-    __shared__ union U { DqShared<2, 4, kFrameSyms> s; DqShared<0, 2> o; __device__ U() {} } sh;
-    if ((int)blockIdx.x < n_other) {
-        decode_quad_body<0, 2>(sh.o, (int)blockIdx.x, n_other, fsym, work, nwork, cap, nullptr, 0, recs, genc, gerr, 1, slot_floats,
+    // (here the stream role's 76 KB leave room for the BERT role on all four waves)
+    __shared__ union U { DqShared<2, 4, kFrameSyms> s; DqShared<0, 2> o; DqShared<4, 4> b; __device__ U() {} } sh;
+    static_assert(sizeof(DqShared<4, 4>) <= sizeof(DqShared<2, 4, kFrameSyms>), "the BERT role must fit the stream role's LDS");
+    const int wg = (int)blockIdx.x;
+    if (wg < n_other) {
+        decode_quad_body<0, 2>(sh.o, wg, n_other, fsym, work, nwork, cap, nullptr, 0, recs, genc, gerr, 1, slot_floats,
                                threadIdx.x >= 128);
+    } else if (wg < n_other + n_bert) {
+        decode_quad_body<4, 4>(sh.b, wg - n_other, n_bert, fsym, work, nwork, cap, nullptr, 0, recs, genc, gerr, 0, slot_floats);
     } else {
-        decode_quad_body<2, 4, kFrameSyms>(sh.s, (int)blockIdx.x - n_other, (int)gridDim.x - n_other, fsym, work, nwork, cap, nullptr, 0,
-                                           recs, genc, gerr, 0, slot_floats);
+        decode_quad_body<2, 4, kFrameSyms>(sh.s, wg - n_other - n_bert, (int)gridDim.x - n_other - n_bert, fsym, work, nwork, cap,
+                                           nullptr, 0, recs, genc, gerr, 0, slot_floats);
     }
 }
 

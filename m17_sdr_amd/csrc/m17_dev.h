@@ -131,11 +131,11 @@ struct DevTables {
     float    mf[kPhases][32];        // matched filter taps, 31 used
     float    md[kPhases][32];        // derivative filter taps
     float    tap_pairs[kPhases][64]; // the same taps as (matched, derivative) pairs, 32 pairs per branch (pair 31 = 0)
-    int16_t  gather[4][488];         // -1 erasure, else src | 0x4000 when negated
+    int16_t  gather[5][488];         // -1 erasure, else src | 0x4000 when negated (row 4: BERT frames)
     int16_t  lich[96];
     DqLich   lich_q[96];             // lich[] as the decoder reads it
     alignas(4) uint8_t regroup[kRegroup];   // stream frame slot: payload symbol (0..183) behind slot entry 8 + i
-    int16_t  glen[4];
+    int16_t  glen[5];
     uint8_t  bm_even[16], bm_odd[16];
     uint16_t crc[256];
 };

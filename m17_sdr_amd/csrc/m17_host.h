@@ -33,14 +33,14 @@ struct Tables {
     uint16_t golay_err[4096];          // m17_golay.cpp:49-72
     float    mf[kPhases][kTaps];       // m17_rx_sync.cpp:114-122 (gain-normalised)
     float    md[kPhases][kTaps];       // m17_rx_sync.cpp:109-119 (central difference)
-    // Per frame type (1 LSF/P1, 2 stream/P2, 3 packet/P3): for each de-punctured
+    // Per frame type (1 LSF/P1, 2 stream/P2, 3 packet/P3, 4 BERT/P2): for each de-punctured
     // position k the index into the 368 demapped soft bits it is fed from, or
     // -1 for an erasure, with the de-randomiser sign folded in.  This is the
     // composition of m17_de_correlate_1 . m17_de_interleave . m17_de_punc_pN
     // (m17_rx_parse.cpp:90-94, :115-135, :165-169).
-    int16_t  gather[4][488];           // [type][k] -> source soft-bit index or -1
-    int8_t   gsign[4][488];            // +1 / -1
-    int16_t  glen[4];                  // 0, 488, 296, 420
+    int16_t  gather[5][488];           // [type][k] -> source soft-bit index or -1
+    int8_t   gsign[5][488];            // +1 / -1
+    int16_t  glen[5];                  // 0, 488, 296, 420, 402 (BERT: entry 401 is the erasure of the unsent bit)
     // Golay part of a stream frame: de-interleaved position j (0..95) <- source
     int16_t  lich_src[96];
     int8_t   lich_sign[96];

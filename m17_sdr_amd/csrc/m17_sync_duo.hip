@@ -420,7 +420,8 @@ void k_sync_frame_duo(const float *__restrict__ disc,     // [C][nblk][384]
                     if (parse && mode == 1) flags |= M17_F_PARSED;
                     const uint32_t w0 = (uint32_t)r.type | ((uint32_t)r.votes << 8) | ((uint32_t)(ferr & 0xFF) << 24);
                     emit_record_wave(crecs, rec_cap, nrec, gl, w0, flags, r.variance, block_count, (uint32_t)(pos - 1));
-                    if ((flags & M17_F_PARSED) && nrec < rec_cap && r.type >= 1 && r.type <= 3) {
+                    // (BERT frames too: the decoder reads them only under the "bert" option, m17_bert.hip)
+                    if ((flags & M17_F_PARSED) && nrec < rec_cap && r.type >= 1 && r.type <= 4) {
                         float *fd = fsym + ((size_t)chan * rec_cap + nrec) * kSlotFloats;
                         store_frame_slot<LPC>(fd, r.type, gl, rg, [&](int q) { return my.H[(fs + q) & (kDuoRing - 1)]; });
                     }

@@ -140,6 +140,26 @@ static void build(Tables &T)
         }
         if (j != kSoftBits) std::abort();
     }
+    // BERT frames (type 4): the inverse of m17_fmt_add_bert_frame (m17_tx_routines.cpp:226-238) -- 197 PRBS9 bits and a
+    // 4-bit zero tail, rate-1/2 coded to 402 bits, P2-punctured to 369 of which the first 368 are sent.  De-punctured
+    // back to 402 (m17_de_punc_p2), coded bit 401 -- kept by P2 -- has no soft bit behind it: the reference's
+    // m17_de_punc_p2(., ., 402) would read soft bit 368, one past the frame.  Here it is an erasure (0.0f).
+    T.glen[4] = 402;
+    {
+        int j = 0;
+        for (int k = 0; k < 402; ++k) {
+            if (puncture_keep(2, k) && j < kSoftBits) {
+                const int src = inv[j++];
+                T.gather[4][k] = (int16_t)src;
+                T.gsign[4][k] = T.derand[src] ? -1 : 1;
+            } else {
+                if (puncture_keep(2, k) && k != 401) std::abort();
+                T.gather[4][k] = -1;
+                T.gsign[4][k] = 1;
+            }
+        }
+        if (j != kSoftBits) std::abort();
+    }
     for (int j = 0; j < 96; ++j) {
         T.lich_src[j] = (int16_t)inv[j];
         T.lich_sign[j] = T.derand[inv[j]] ? -1 : 1;

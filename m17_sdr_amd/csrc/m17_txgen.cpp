@@ -423,6 +423,98 @@ int m17gen_channel(const m17gen_params *p, int nblk, int16_t *h_iq,
     return sent;
 }
 
+// m17_fmt_add_bert_frame, m17_tx_routines.cpp:226-238: m17_prbs9_tx_load of 197 bits (m17_prbs9.cpp:28-33 over the
+// sequence of generate_prbs9 :16-27), the zero tail, m17_conv_encode_1 over 201 bits, P2 to 369 bits of which the frame
+// carries the first 368
+int m17gen_bert_frame_dibits(uint16_t *prbs_idx, uint8_t dibits[192])
+{
+    if (!prbs_idx || !dibits || *prbs_idx >= 511) return M17GPU_ERR_ARG;
+    static const auto seq = [] {
+        std::vector<uint8_t> q(511);
+        unsigned sr = 1;
+        for (int i = 0; i < 511; ++i) {
+            const unsigned bit = ((sr >> 8) ^ (sr >> 4)) & 1u;
+            sr = ((sr << 1) | bit) & 0x1FFu;
+            q[(size_t)i] = (uint8_t)bit;
+        }
+        return q;
+    }();
+    const Tables &T = tables();
+    uint8_t in[201], coded[402], bits[369];
+    for (int i = 0; i < 197; ++i) { in[i] = seq[*prbs_idx]; *prbs_idx = (uint16_t)((*prbs_idx + 1) % 511); }
+    std::memset(&in[197], 0, 4);
+    unsigned sr = 0;                                              // m17_conv_encode_1 (m17_conv.cpp:33-49)
+    for (int i = 0; i < 201; ++i) {
+        if (in[i]) sr |= 0x10;
+        coded[2 * i] = T.clut[sr][0];
+        coded[2 * i + 1] = T.clut[sr][1];
+        sr >>= 1;
+    }
+    if (puncture(2, coded, 402, bits) != 369) return -1;
+    finish_frame(m17::kSyncBert, bits, dibits);
+    return 192;
+}
+
+// one channel of m17gen_bert_batch: the framing of m17gen_channel with BERT frames in place of LSF + stream frames
+static int bert_channel(uint64_t seed, int delay, float ebn0_db, float noise_cutoff_hz, int nblk, int n_bert_frames, int16_t *h_iq)
+{
+    const size_t want = (size_t)nblk * m17::kBlockSamples;
+    std::vector<int16_t> iq;
+    iq.reserve(2 * (want + 4096));
+    Transmitter tx(iq, want);
+    for (int i = 0; i < delay; ++i) { iq.push_back(0x3FFF); iq.push_back(0); }
+    int sent = 0;
+    uint8_t d[192];
+    while (!tx.full()) {
+        tx.carrier(192);                                          // as m17gen_channel: carrier, two preambles (m17_tx_rx.cpp:95-97)
+        tx.preamble();
+        tx.preamble();
+        uint16_t idx = 0;                                         // m17_prbs9_tx_reset before a BERT transmission
+        for (int f = 0; f < n_bert_frames && !tx.full(); ++f) {
+            if (m17gen_bert_frame_dibits(&idx, d) != 192) return -1;
+            tx.send_dibits(d, 192);
+            ++sent;
+        }
+        tx.eot();
+    }
+    iq.resize(2 * want);
+    if (ebn0_db < 100.0f) {                                       // as m17gen_channel
+        const double esn0 = 2.0 * std::pow(10.0, ebn0_db / 10.0);
+        const double a = 16383.0;
+        const double sigma = std::sqrt(a * a * kOs / (2.0 * esn0));
+        SplitMix64 nrng(seed ^ 0xA36E0000A36E0000ull);
+        add_awgn(iq, sigma, nrng, (double)noise_cutoff_hz);
+    }
+    std::memcpy(h_iq, iq.data(), sizeof(int16_t) * 2 * want);
+    return sent;
+}
+
+int m17gen_bert_batch(int C, uint64_t base_seed, int first_channel, int nblk, int n_bert_frames,
+                      float ebn0_db, float noise_cutoff_hz, int16_t *h_iq, int32_t *h_nframes, int nthreads)
+{
+    if (C <= 0 || nblk <= 0 || n_bert_frames <= 0 || !h_iq) return M17GPU_ERR_ARG;
+    if (nthreads < 1) nthreads = 1;
+    nthreads = std::min(nthreads, C);
+    std::vector<std::thread> pool;
+    std::vector<int> status((size_t)nthreads, 0);
+    const size_t chan_stride = (size_t)nblk * m17::kBlockSamples * 2;
+    for (int t = 0; t < nthreads; ++t) {
+        pool.emplace_back([=, &status] {
+            for (int c = t; c < C; c += nthreads) {
+                const uint64_t ch = (uint64_t)(first_channel + c);
+                SplitMix64 h(0xD1B54A32D192ED03ull ^ (ch * 0x9E3779B97F4A7C15ull));     // the delay of m17gen_batch
+                const int r = bert_channel(base_seed + ch, (int)(h.next() % 1920), ebn0_db, noise_cutoff_hz, nblk, n_bert_frames,
+                                           h_iq + (size_t)c * chan_stride);
+                if (r < 0) status[(size_t)t] = r;
+                else if (h_nframes) h_nframes[c] = r;
+            }
+        });
+    }
+    for (auto &th : pool) th.join();
+    for (int s : status) if (s < 0) return s;
+    return 0;
+}
+
 int m17gen_batch(int C, uint64_t base_seed, int first_channel, int nblk, int n_stream_frames,
                  float ebn0_db, float noise_cutoff_hz, int packet_mode, int16_t *h_iq, uint8_t *h_lsf,
                  uint8_t *h_payload, int max_payload_frames, int32_t *h_nframes, int nthreads)

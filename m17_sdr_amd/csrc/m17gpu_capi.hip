@@ -7,6 +7,7 @@
 #include "m17_sync_wave.hip"
 #include "m17_fused.hip"
 #include "m17_decode_quad.hip"
+#include "m17_bert.hip"
 #include "m17_book.hip"
 #include "m17_pack.hip"
 #include "m17_pluto.hip"
@@ -66,6 +67,10 @@ struct m17gpu_ctx {
     int fir_impl = 0;                        // 0 = by call (fir_choice); 1 = front end + timing kernel; 4 = wave per channel over sixteen-row
                                              // tiles of its own blocks, rows through the workspace, six waves per SIMD (k_rx_chan6);
                                              // 5 = three waves per channel, the front end one of them (k_sync_frame_duo<1>, up to 1,024 channels)
+    int bert = 0;                            // 1 = BERT receive ("bert" option): type-4 frames decoded and fed to the PRBS9 checker
+    BertChan *d_bert = nullptr;              // [C] PRBS9 checker state and counters (m17_bert.hip)
+    int32_t *d_bert_away = nullptr;          // [2] some checker away from its reset state after the previous call (k_bert_chain);
+    int bert_par = 0;                        //     the word the next call reads, the other one it writes
     bool nwork_dirty = false;                // a full-chain call got past k_worklist but not to the bookkeeping kernel that zeroes the counters
     int last_path[4] = {0, 0, 0, 0};         // what the last m17gpu_rx_blocks call ran: FIR stage (fir_choice), plain slots, bookkeeping kernel, (reserved)
     std::vector<hipEvent_t> ev_pool;         // 7 events per profiled call: 5 stage marks + call start / end
@@ -116,7 +121,7 @@ int upload_tables(m17gpu_ctx *ctx)
             h.mf[p][j] = T.mf[p][j]; h.md[p][j] = T.md[p][j];
             h.tap_pairs[p][2 * j] = T.mf[p][j]; h.tap_pairs[p][2 * j + 1] = T.md[p][j];
         }
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < 5; ++t) {
         h.glen[t] = T.glen[t];
         for (int k = 0; k < 488; ++k) {
             int16_t g = T.gather[t][k];
@@ -296,12 +301,12 @@ int launch_decode(m17gpu_ctx *ctx, m17gpu_rec *d_recs, int rec_cap, int32_t *d_c
     m17gpu_rec_dev *recs = reinterpret_cast<m17gpu_rec_dev *>(d_recs) + (size_t)c0 * rec_cap;
     int32_t *cnt = (d_counts ? d_counts : ctx->d_counts) + c0;
     float *fsym = ctx->d_fsym + (size_t)c0 * rec_cap * kSlotFloats;
-    int32_t *work = ctx->d_work + 3 * (size_t)c0 * ctx->rec_cap_max;
+    int32_t *work = ctx->d_work + 4 * (size_t)c0 * ctx->rec_cap_max;
     int32_t *nwork = ctx->d_nwork + 4 * chunk;
     const long long slots = (long long)cn * rec_cap;
     ctx->nwork_dirty = true;                        // until the bookkeeping kernel, which zeroes the counters, is enqueued
     hipLaunchKernelGGL(k_worklist, dim3(cdiv(slots, 1024)), dim3(1024), 0, st, recs, rec_cap, cnt, cn,
-                       work, nwork, (int)slots);
+                       work, nwork, (int)slots, ctx->bert ? 4 : 3, ctx->bert ? ctx->d_bert_away + (ctx->bert_par ^ 1) : nullptr);
     // one launch for all three lists (k_decode_lists): stream frames, the bulk of any traffic, on five workgroups of
     // four waves per CU (30.5 KB of LDS and 96 VGPRs each); link-setup and packet frames on up to 512 leading workgroups
     const int tasks = cdiv(slots, DQ_FRAMES) + 2;
@@ -309,15 +314,28 @@ int launch_decode(m17gpu_ctx *ctx, m17gpu_rec *d_recs, int rec_cap, int32_t *d_c
     if (n_other > 512) n_other = 512;
     int grid = cdiv(tasks, 4);
     if (grid > 256 * 5) grid = 256 * 5;             // (four or three workgroups per CU: 0.177-0.180 -> 0.196-0.200 / 0.191 ms, round 4)
+    // the BERT role ("bert" option): sized like the stream role, on its three (plain slots: four) waves per workgroup
+    int n_bert = 0;
+    if (ctx->bert) {
+        n_bert = cdiv(tasks, plain ? 4 : DQ_BERT_WAVES);
+        if (n_bert > 256 * (plain ? 2 : 5)) n_bert = 256 * (plain ? 2 : 5);
+    }
     if (plain) {
         int gp = cdiv(tasks, 4);
         if (gp > 256 * 2) gp = 256 * 2;             // 76 KB of LDS per workgroup: two per CU
-        hipLaunchKernelGGL(k_decode_lists_p, dim3(gp + n_other), dim3(256), 0, st, fsym, work, nwork, (int)slots, recs,
-                           ctx->d_genc, ctx->d_gerr, kSlotFloats, n_other);
+        hipLaunchKernelGGL(k_decode_lists_p, dim3(gp + n_other + n_bert), dim3(256), 0, st, fsym, work, nwork, (int)slots, recs,
+                           ctx->d_genc, ctx->d_gerr, kSlotFloats, n_other, n_bert);
     } else
-    hipLaunchKernelGGL(k_decode_lists, dim3(grid + n_other), dim3(256), 0, st, fsym, work, nwork, (int)slots, recs,
-                       ctx->d_genc, ctx->d_gerr, kSlotFloats, n_other);
+    hipLaunchKernelGGL(k_decode_lists, dim3(grid + n_other + n_bert), dim3(256), 0, st, fsym, work, nwork, (int)slots, recs,
+                       ctx->d_genc, ctx->d_gerr, kSlotFloats, n_other, n_bert);
     HIPCHK(hipGetLastError());
+    // the PRBS9 checker over the decoded BERT frames, in record order (before the bookkeeping kernel zeroes nwork[3])
+    if (ctx->bert) {
+        hipLaunchKernelGGL(k_bert_chain, dim3(cdiv(cn, BC_CH)), dim3(BC_THREADS), 0, st, recs, rec_cap, cnt, cn,
+                           ctx->d_bert + c0, nwork, ctx->d_bert_away + ctx->bert_par, ctx->d_bert_away + (ctx->bert_par ^ 1));
+        ctx->bert_par ^= 1;
+        HIPCHK(hipGetLastError());
+    }
     if (ev_mid) HIPCHK(hipEventRecord(ev_mid, st));
     // bookkeeping: a lane per channel (k_book_lanes) for large batches -- it is ~25 us whatever the batch, the wave-per-channel
     // kernel 19 us at 4,096 channels x 16 blocks, 28 at 8,192, 42 at 16,384, 80 at 32,768 -- unless the network sink is attached
@@ -374,7 +392,9 @@ int m17gpu_create(m17gpu_ctx **out, int n_channels, int max_blocks, int device)
     ALLOC(ctx->d_disc, sizeof(float) * cb * kDiscOut);
     ALLOC(ctx->d_offs, sizeof(float) * cb);
     ALLOC(ctx->d_fsym, sizeof(float) * (size_t)n_channels * ctx->rec_cap_max * kSlotFloats);
-    ALLOC(ctx->d_work, sizeof(int32_t) * 3 * (size_t)n_channels * ctx->rec_cap_max);   // one list per frame type (decode_impl 2)
+    ALLOC(ctx->d_work, sizeof(int32_t) * 4 * (size_t)n_channels * ctx->rec_cap_max);   // one list per frame type (decode_impl 2), BERT the fourth
+    ALLOC(ctx->d_bert, sizeof(BertChan) * (size_t)n_channels);
+    ALLOC(ctx->d_bert_away, 2 * sizeof(int32_t));
     ALLOC(ctx->d_nwork, sizeof(int32_t) * 8);
     ALLOC(ctx->d_counts, sizeof(int32_t) * (size_t)n_channels);
     ALLOC(ctx->d_dec_hist, sizeof(uint32_t) * 32 * (size_t)n_channels);
@@ -397,7 +417,8 @@ void m17gpu_destroy(m17gpu_ctx *ctx)
     if (!ctx) return;
     DeviceScope dev_scope_(ctx->device);
     void *bufs[] = {ctx->d_state, ctx->d_disc, ctx->d_offs, ctx->d_fsym, ctx->d_work,
-                    ctx->d_nwork, ctx->d_counts, ctx->d_genc, ctx->d_gerr, ctx->d_crc_basis, ctx->d_dec_hist, ctx->d_flags};
+                    ctx->d_nwork, ctx->d_counts, ctx->d_genc, ctx->d_gerr, ctx->d_crc_basis, ctx->d_dec_hist, ctx->d_flags,
+                    ctx->d_bert, ctx->d_bert_away};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     delete ctx;
@@ -412,6 +433,10 @@ int m17gpu_reset(m17gpu_ctx *ctx, void *stream)
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(ctx->d_dec_hist, 0, sizeof(uint32_t) * 32 * (size_t)ctx->C, S(stream)));
     HIPCHK(hipMemsetAsync(ctx->d_nwork, 0, sizeof(int32_t) * 8, S(stream)));
+    // the PRBS9 checkers as the reference starts them: every static 0 (m17_prbs9.cpp:6-12), idx 0, NO_SYNC
+    HIPCHK(hipMemsetAsync(ctx->d_bert, 0, sizeof(BertChan) * (size_t)ctx->C, S(stream)));
+    HIPCHK(hipMemsetAsync(ctx->d_bert_away, 0, 2 * sizeof(int32_t), S(stream)));
+    ctx->bert_par = 0;
     ctx->nwork_dirty = false;
     return M17GPU_OK;
 }
@@ -600,6 +625,7 @@ int m17gpu_set_option(m17gpu_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "afc")) { if (value != 0 && value != 1) return bad(); ctx->afc = value; }
     else if (!std::strcmp(name, "slot_impl")) { if (value < 0 || value > 2) return bad(); ctx->slot_impl = value; }
     else if (!std::strcmp(name, "book_impl")) { if (value < 0 || value > 2) return bad(); ctx->book_impl = value; }
+    else if (!std::strcmp(name, "bert")) { if (value != 0 && value != 1) return bad(); ctx->bert = value; }
 #ifdef M17_STAMPS
     else if (!std::strcmp(name, "fe_debug")) { ctx->fe_debug = value; }      // instrumented build only: WRONG results
 #endif
@@ -1187,8 +1213,40 @@ int m17gpu_decode_frames(m17gpu_ctx *ctx, const float *d_sym, const uint8_t *d_t
     if (grid > 256 * 2) grid = 256 * 2;
     hipLaunchKernelGGL(k_decode_quad<0>, dim3(grid), dim3(256), 0, st, d_sym, (const int32_t *)nullptr,
                        (const int32_t *)nullptr, 0, d_type, n, reinterpret_cast<m17gpu_rec_dev *>(d_recs),
-                       ctx->d_genc, ctx->d_gerr, 0, kFrameSyms);
+                       ctx->d_genc, ctx->d_gerr, 0, kFrameSyms, ctx->bert);
     HIPCHK(hipGetLastError());
+    return M17GPU_OK;
+}
+
+// The PRBS9 checker of the "bert" option on a caller's streams (m17_bert.hip, k_bert_feed): the channels' checker state is
+// the one the full chain uses, and is carried on.
+int m17gpu_bert_feed(m17gpu_ctx *ctx, const uint8_t *d_bits, const uint8_t *d_kind, int n, uint8_t *d_out, void *stream)
+{
+    if (!ctx || !d_bits || !d_kind || !d_out || n <= 0) return fail(M17GPU_ERR_ARG, "m17gpu_bert_feed: bad argument");
+    ON_CTX_DEVICE(ctx);
+    hipLaunchKernelGGL(k_bert_feed, dim3(cdiv(ctx->C, BC_CH)), dim3(BC_THREADS), 0, S(stream), d_bits, d_kind, n, ctx->C,
+                       ctx->d_bert, d_out, ctx->d_bert_away + ctx->bert_par);
+    HIPCHK(hipGetLastError());
+    return M17GPU_OK;
+}
+
+// counters [C][6]: bits checked in sync, errors among them, BERT frames decoded, frames erased, locks, losses;
+// state [C][6]: m_rx_idx, m_rx_state, m_rx_bad, m_rx_good, m_rx_eq_cnt, m_rx_dif_cnt (m17_prbs9.cpp:6-12)
+int m17gpu_get_bert(m17gpu_ctx *ctx, uint64_t *h_cnt, int32_t *h_state)
+{
+    if (!ctx) return fail(M17GPU_ERR_ARG, "m17gpu_get_bert: null context");
+    ON_CTX_DEVICE(ctx);
+    std::vector<BertChan> h((size_t)ctx->C);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h.data(), ctx->d_bert, sizeof(BertChan) * (size_t)ctx->C, hipMemcpyDeviceToHost));
+    for (int c = 0; c < ctx->C; ++c) {
+        const BertChan &b = h[c];
+        if (h_cnt) for (int k = 0; k < 6; ++k) h_cnt[6 * (size_t)c + k] = b.cnt[k];
+        if (h_state) {
+            int32_t *a = h_state + 6 * (size_t)c;
+            a[0] = b.idx; a[1] = b.state; a[2] = b.bad; a[3] = b.good; a[4] = b.eq; a[5] = b.dif;
+        }
+    }
     return M17GPU_OK;
 }
 
